@@ -25,6 +25,18 @@ HIP AdamW launch, hand-written HIP GEMM / LayerNorm / bias-GELU / cross-entropy 
 MFMA flash-attention kernels. Synthetic tokens, random init, fixed work per GPU
 (weak scaling). The K timed steps are bracketed by barrier + synchronize, time =
 max over ranks; one JSON line is printed.
+
+A plain run does only that: set-up, ``--warmup`` steps, the ``--steps`` timed
+steps, the result line (``ms_per_step`` = wall time of one timed step).
+``--dump-outputs DIR`` also writes, after the timed steps, what the last timed
+step computed: ``DIR/loss.npy`` (its loss, one value per rank) and
+``DIR/params_sample.npy`` (a fixed seeded sample of the weights it left, float32,
+about 10 MB for GPT-2-XL). Weights, tokens and sample indices are seeded, so with
+the same arguments two builds can be compared output for output; two GPU runs of
+one build agree to the rounding of the kernels' unordered float atomics (measured
+after 4 steps: loss within 3e-5, weights within one bf16 ulp), CPU runs exactly.
+``--full`` is where any measurement beyond the headline figure belongs; there is
+none today.
 """
 from __future__ import annotations
 
@@ -52,8 +64,50 @@ def parse(argv=None):
     ap.add_argument("--bucket-mb", type=float, default=None)
     ap.add_argument("--zero", type=int, default=int(os.environ.get("CAAMD_ZERO", "1")),
                     help="1 = ZeRO-1 sharded optimizer when world > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss per "
+                         "rank and a fixed seeded sample of the updated weights) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (none today: a plain run "
+                         "already does only set-up, warm-up and the timed steps)")
     ap.add_argument("--cpu", action="store_true", help=argparse.SUPPRESS)  # gloo/CPU rehearsal (tests)
     return ap.parse_args(argv)
+
+
+DUMP_SEED = 20240607
+DUMP_PER_PARAM = 8192  # sampled elements per parameter: GPT-2-XL's 580 parameters -> 10 MB of float32
+
+
+def dump_outputs(out_dir, step, loss, world, rank):
+    """What a caller of the timed path holds after its last step: the loss that step
+    returned (one per rank) and the weights it left behind. The weights are sampled
+    per parameter, in the parameter's logical element order and at indices drawn from
+    a fixed seed, so two builds are compared element for element whatever their
+    storage layout. Rank 0 writes; the weights are the same on every rank."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    step.wait_params()
+    losses = loss.detach().float().reshape(1)
+    if world > 1:
+        parts = [torch.empty_like(losses) for _ in range(world)]
+        dist.all_gather(parts, losses)
+        losses = torch.cat(parts)
+    if rank != 0:
+        return
+    rng = np.random.default_rng(DUMP_SEED)
+    chunks = []
+    with torch.no_grad():
+        for _name, p in sorted(step.model.named_parameters(), key=lambda kv: kv[0]):
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_PER_PARAM:
+                idx = np.sort(rng.choice(flat.numel(), DUMP_PER_PARAM, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            chunks.append(flat.float().cpu())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), losses.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(chunks).numpy().astype(np.float32))
 
 
 def train_loop_per_worker(cfg):
@@ -104,10 +158,13 @@ def train_loop_per_worker(cfg):
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    peak_mem_gb = (torch.cuda.max_memory_allocated(device) / 2**30) if on_gpu else 0.0
+    if cfg.get("dump_outputs"):
+        dump_outputs(cfg["dump_outputs"], step, last, world, rank)
     train.report({
         "dt": dt, "loss": float(last.item()), "world": world, "params": model.num_params(),
         "flops_per_token": model.flops_per_token(T), "zero": step.zero, "pid": os.getpid(),
-        "peak_mem_gb": (torch.cuda.max_memory_allocated(device) / 2**30) if on_gpu else 0.0,
+        "peak_mem_gb": peak_mem_gb,
     })
 
 
@@ -131,7 +188,8 @@ def run(argv=None):
     launcher_rank = int(os.environ.get("RANK", "0")) if launched else 0
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cfg = {"model": args.model, "micro_batch": args.micro_batch, "seq_len": args.seq_len,
-           "warmup": args.warmup, "steps": args.steps, "bucket_mb": args.bucket_mb, "zero": args.zero}
+           "warmup": args.warmup, "steps": args.steps, "bucket_mb": args.bucket_mb, "zero": args.zero,
+           "dump_outputs": os.path.abspath(args.dump_outputs) if args.dump_outputs else None}
 
     if args.mode == "actor":
         if launched and launcher_rank != 0:

@@ -43,6 +43,37 @@ def test_bench_actor_mode_world2_cpu():
     assert j["config"]["global_batch"] == 4
 
 
+def test_bench_dump_outputs_repeatable_cpu(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's loss and weight sample as
+    float32 ``.npy`` (64 MB at the most) and, on CPU, the same arguments give the same
+    arrays in two runs (seeded weights, tokens and sample indices). ``--steps`` sets
+    the timed steps, ``--full`` is accepted, and the result line is still the only one."""
+    import numpy as np
+
+    args = ["--cpu", "--model", "gpt2-tiny", "--micro-batch", "2", "--seq-len", "32", "--warmup", "1"]
+    dumps = []
+    for name, extra in (("a", ["--steps", "2"]), ("b", ["--steps", "2", "--full"]), ("c", ["--steps", "3"])):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args, *extra,
+                            "--dump-outputs", str(d)],
+                           cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        assert lines[0]["steps"] == int(extra[1]) and lines[0]["ms_per_step"] > 0
+        assert sorted(p.name for p in d.iterdir()) == ["loss.npy", "params_sample.npy"]
+        arrs = {p.name: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        assert arrs["loss.npy"].shape == (1,) and arrs["params_sample.npy"].size > 1000
+        assert abs(float(arrs["loss.npy"][0]) - lines[0]["final_loss"]) < 1e-3
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    # one more timed step: another batch, another update
+    assert not np.array_equal(dumps[0]["params_sample.npy"], dumps[2]["params_sample.npy"])
+
+
 def test_bench_actor_mode_under_launcher_prints_once():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29641",

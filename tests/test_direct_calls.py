@@ -58,6 +58,17 @@ def _direct_client(actor):
     return dc if dc is not None and not isinstance(dc, tuple) else None
 
 
+def _call_until_direct(actor, limit_s=30.0):
+    """Call the actor until this caller has switched it to the direct transport.
+    The switch happens at a call made with no head-routed call in flight and at
+    least 50 ms after a lookup that found the actor not yet alive, so on a fast
+    machine (pre-forked workers) the second call can still take the head path."""
+    deadline = time.monotonic() + limit_s
+    while _direct_client(actor) is None and time.monotonic() < deadline:
+        ray.get(actor.pid.remote())
+    return _direct_client(actor)
+
+
 def test_order_preserved_across_switch(cluster):
     a = Log.remote()
     refs = [a.add.remote(i) for i in range(300)]  # early calls may go through the head
@@ -113,7 +124,7 @@ def test_actor_death_without_retries_fails_calls(cluster):
     a = Log.options(max_restarts=0).remote()
     pid = ray.get(a.pid.remote())
     ray.get(a.pid.remote())
-    assert _direct_client(a) is not None
+    assert _call_until_direct(a) is not None
     slow = [a.slow_add.remote(i) for i in range(50)]
     os.kill(pid, signal.SIGKILL)
     errors = 0
